@@ -21,10 +21,17 @@ in [1, 5], LeastAllocated or MostAllocated), each over the full queue on its
 own copy of the cluster (weak scaling: per-GPU work fixed; no data-path
 collective).  value = pods scheduled by all ranks / max-over-ranks time; one
 RCCL all_gather of every replica's placements per step.  The process group is
-RCCL ("nccl") at every N, N = 1 included (a one-rank group on 127.0.0.1), so
+RCCL ("nccl") at every N, N = 1 included (a one-rank group over a file store), so
 the collective runs on the box.
 
-Prints ONE JSON line (rank 0).  The line also carries:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the
+steps and prints the headline with the whole step's roofline (device time of
+the timed steps); `--dump-outputs DIR` also writes the last timed step's
+placements to DIR/placements.npy and the gathered replicas' to
+DIR/replica_placements.npy (float64; the queue is generated from fixed seeds,
+so two builds can be compared output for output).  With `--full` the
+headline's roofline is its dominant kernel's (one extra step under per-kernel
+HIP-event timing) and the line also carries:
 * `configs1`: BASELINE configs[1] (5,000 x 50,000, NodeResourcesFit +
   BalancedAllocation + TaintToleration + NodeAffinity, generator.config2) with
   its own roofline, PMC traffic and CPU baseline (the rounds 1-4 headline);
@@ -474,7 +481,8 @@ def queue_roofline(metrics, kstats, bpe: int, node_evals: int, kms: float, pmc_f
     # per step, phase 1 / top-k beside it); the per-kernel pass runs with HIP
     # events around every launch, which takes the one-launch-per-batch form of
     # the same walk on one stream
-    roof["timing_pass"] = "per-batch launches, one stream (ksg_set_timing); timed steps: persistent walk"
+    roof["timing_pass"] = ("per-batch launches, one stream (ksg_set_timing); timed steps: persistent walk"
+                           if kstats else "none (--full runs it): the whole step, device time of the timed steps")
     # HBM bytes per launch of the dominant kernel from the committed PMC passes
     # (profiles/run_pmc.sh -> profiles/pmc_summary.py: 2 x FETCH_SIZE +
     # WRITE_SIZE per dispatch, gfx950-corrected), null when not collected
@@ -622,7 +630,20 @@ def main():
     ap.add_argument("--topo-annotate-pods", type=int, default=256, help="configs[2] annotation leg; 0 disables")
     ap.add_argument("--no-build-check", action="store_true",
                     help="skip the check that libksched.so embeds the tree's source hash")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg of the line: the per-kernel timing pass "
+                         "(roofline of the dominant kernel), configs[1], the replica sweep, the annotation, "
+                         "per-cycle, configs[2] and kubelet-memory legs and the CPU baselines (the options above "
+                         "that size or disable a leg apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64): placements.npy, "
+                         "rank 0's placements of the queue, and replica_placements.npy, every rank's placements "
+                         "as the RCCL all_gather delivered them")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     # Before anything touches the GPU: the library must be built from this
     # tree's source, and `--gpus N` without a launcher starts N ranks here
@@ -648,17 +669,22 @@ def main():
     import numpy as np
     import torch
     import torch.distributed as dist
-    if "MASTER_ADDR" not in os.environ:   # N = 1 without a launcher: a one-rank RCCL group
-        import socket
-        sk = socket.socket()
-        sk.bind(("127.0.0.1", 0))
-        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(sk.getsockname()[1]), RANK="0",
-                          WORLD_SIZE="1", LOCAL_RANK="0")
-        sk.close()
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
-    dist.init_process_group(backend="nccl", init_method="env://", world_size=world, rank=rank,
-                            device_id=torch.device(dev))
+    if "MASTER_ADDR" not in os.environ:
+        # N = 1 without a launcher: a one-rank RCCL group over a file store of
+        # its own (no TCP port to pick: a port found free and bound later can
+        # be taken in between by another run on the same host)
+        import atexit
+        import shutil
+        import tempfile
+        store_dir = tempfile.mkdtemp(prefix="ksg_bench_store_")
+        atexit.register(shutil.rmtree, store_dir, ignore_errors=True)   # also when the run ends in an error
+        dist.init_process_group(backend="nccl", store=dist.FileStore(os.path.join(store_dir, "store"), 1),
+                                world_size=1, rank=0, device_id=torch.device(dev))
+    else:
+        dist.init_process_group(backend="nccl", init_method="env://", world_size=world, rank=rank,
+                                device_id=torch.device(dev))
     # one collective before the library opens its streams: RCCL creates its
     # own streams at the first collective, and with GPU_MAX_HW_QUEUES = 4 the
     # order decides which streams share a hardware queue; opened after RCCL's,
@@ -731,19 +757,27 @@ def main():
     import hashlib
     replica_digest = hashlib.sha256(b"".join(g.cpu().numpy().tobytes() for g in gather_out)).hexdigest()
     distinct = len({hashlib.sha256(g.cpu().numpy().tobytes()).hexdigest() for g in gather_out})
-    # one extra, untimed step with per-kernel HIP-event timing (ksg_set_timing)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: this rank's placements
+        # (node index per pod, -1 unschedulable) and the gathered replicas'
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "placements.npy"), np.asarray(pl, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "replica_placements.npy"),
+                np.stack([g.cpu().numpy() for g in gather_out]).astype(np.float64))
+    # --full: one extra, untimed step with per-kernel HIP-event timing (ksg_set_timing)
     kstats = []
-    try:
-        eng.set_timing(True)
-        step()
-        kstats = eng.kernel_stats()
-        eng.set_timing(False)
-    except Exception as e:   # timing is diagnostic; never lose the bench line over it
-        log(f"[rank {rank}] per-kernel timing unavailable: {e}")
+    if args.full:
+        try:
+            eng.set_timing(True)
+            step()
+            kstats = eng.kernel_stats()
+            eng.set_timing(False)
+        except Exception as e:   # timing is diagnostic; never lose the bench line over it
+            log(f"[rank {rank}] per-kernel timing unavailable: {e}")
 
-    # ---- configs[1] and the legs on its cluster ----------------------------------------
+    # ---- configs[1] and the legs on its cluster (--full) -------------------------------
     c1 = eng1 = enc1 = prof1 = None
-    if args.configs1_pods > 0:
+    if args.full and args.configs1_pods > 0:
         try:
             c1, eng1, enc1, prof1 = configs1_line(native, G, E, metrics, args.nodes, args.configs1_pods, 2,
                                                   0.0 if args.no_cpu_baseline or world > 1 else 8.0, local_rank)
@@ -770,7 +804,7 @@ def main():
     if eng1 is not None:
         eng1.close()
     cyc = cyc_launch = cyc_hint = None
-    if world == 1 and args.cycle_pods > 0:
+    if args.full and world == 1 and args.cycle_pods > 0:
         try:
             S = importlib.import_module(PKG + ".snapshot")
             cyc = per_cycle_sidecar(native, G, S, args.nodes, args.cycle_warm, args.cycle_pods)
@@ -780,14 +814,14 @@ def main():
         except Exception as e:
             log(f"[rank {rank}] per-cycle sidecar unavailable: {e}")
     cyc3 = ann3 = None
-    if world == 1 and args.topo_cycle_pods > 0:
+    if args.full and world == 1 and args.topo_cycle_pods > 0:
         try:
             S = importlib.import_module(PKG + ".snapshot")
             cyc3 = per_cycle_sidecar(native, G, S, args.topo_nodes, 300, args.topo_cycle_pods, make=G.config3,
                                      label="configs[2]")
         except Exception as e:
             log(f"[rank {rank}] configs[2] per-cycle sidecar unavailable: {e}")
-    if world == 1 and args.topo_annotate_pods > 0:
+    if args.full and world == 1 and args.topo_annotate_pods > 0:
         try:
             B = importlib.import_module(PKG + ".bulk")
             n3, p3, prof3 = G.config3(n_nodes=args.topo_nodes, n_pods=args.topo_annotate_pods)
@@ -808,7 +842,7 @@ def main():
         except Exception as e:
             log(f"[rank {rank}] configs[2] annotation sidecar unavailable: {e}")
     topo = None
-    if world == 1 and args.topo_queue_pods > 0:
+    if args.full and world == 1 and args.topo_queue_pods > 0:
         try:
             topo = topo_queue_line(native, G, E, metrics, args.topo_nodes, args.topo_queue_pods)
         except Exception as e:
@@ -853,7 +887,7 @@ def main():
                          ("annotations_configs2", ann3)):
             if val is not None:
                 out[key] = val
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baselines(enc, pf, args.cpu_budget, check=pl)
             # the headline's placements against the oracle over the whole queue
             out["placements_equal_oracle"] = out["cpu_baseline"].get("placements_equal_oracle")

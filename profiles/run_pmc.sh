@@ -16,7 +16,7 @@ export TMPDIR=/tmp
 ( while sleep 45; do date >> "$OUT/heartbeat.txt"; done ) &
 HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
-B="python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 --configs1-pods 0 --sweep-replicas 0 --annotate-pods 0 --cycle-pods 0 --kubelet-pods 0 --topo-cycle-pods 0 --topo-annotate-pods 0"
+B="python3 bench.py --steps 2 --warmup 1"   # a plain run: the headline alone
 B1="$B --workload configs1"
 S="python3 scripts/bench_configs.py --config 4 --replicas 1024 --pods 256 --reps 1 --no-cpu-baseline"
 SP="$S --no-timing"

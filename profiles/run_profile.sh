@@ -6,4 +6,4 @@ OUT=${1:-gpurun_out/prof}; shift || true
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run -- \
-  python3 bench.py --no-cpu-baseline "$@"
+  python3 bench.py "$@"

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-exit_bisect}
 mkdir -p "$O"
 export TMPDIR=/tmp
-Z="--no-cpu-baseline --steps 1 --warmup 1 --configs1-pods 0 --sweep-replicas 0 --annotate-pods 0 --cycle-pods 0 --kubelet-pods 0 --topo-cycle-pods 0 --topo-annotate-pods 0"
+Z="--full --no-cpu-baseline --steps 1 --warmup 1 --configs1-pods 0 --sweep-replicas 0 --annotate-pods 0 --cycle-pods 0 --kubelet-pods 0 --topo-cycle-pods 0 --topo-annotate-pods 0"
 leg() {
   local name=$1; shift
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/$name" -o run -- python3 -u bench.py $Z "$@" > "$O/$name.log" 2>&1

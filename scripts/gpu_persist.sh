@@ -8,7 +8,7 @@ mkdir -p "$O"
 timeout -k 10 600 python3 -u -m pytest -x -v --timeout 200 --timeout-method thread -m gpu tests/test_gpu_headline.py \
   tests/test_gpu_batch_variants.py tests/test_gpu_parity.py tests/test_gpu_recovery.py > "$O/tests.log" 2>&1 || { echo "tests failed"; tail -30 "$O/tests.log"; exit 1; }
 tail -1 "$O/tests.log"
-B="python3 -u bench.py --steps 5 --warmup 1 --no-cpu-baseline --sweep-replicas 0 --annotate-pods 0 --cycle-pods 0 --kubelet-pods 0 --topo-cycle-pods 0 --topo-queue-pods 0 --topo-annotate-pods 0"
+B="python3 -u bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --sweep-replicas 0 --annotate-pods 0 --cycle-pods 0 --kubelet-pods 0 --topo-cycle-pods 0 --topo-queue-pods 0 --topo-annotate-pods 0"
 for r in 1 2; do
   for m in 0 1; do
     KSG_SPEC_PERSIST=$m timeout -k 10 300 $B > "$O/p${m}_$r.json" 2> "$O/p${m}_$r.err" || { echo "run $m $r failed"; tail -5 "$O/p${m}_$r.err"; exit 1; }

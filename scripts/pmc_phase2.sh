@@ -4,7 +4,7 @@ set -uo pipefail
 OUT=${1:-gpurun_out/pmc_p2}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 bench.py --no-cpu-baseline --steps 1 --warmup 0 --pods 5120 --sweep-replicas 0"
+B="python3 bench.py --steps 1 --warmup 0 --pods 5120"   # a plain run: the headline alone
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d "$OUT/a" -o run -- $B > "$OUT/a.log" 2>&1 || { tail -5 "$OUT/a.log"; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_SMEM SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_INSTS_BRANCH SQ_INSTS_VMEM --output-format csv -d "$OUT/b" -o run -- $B > "$OUT/b.log" 2>&1 || { tail -5 "$OUT/b.log"; exit 1; }
 python3 - "$OUT" <<'PY'

@@ -61,12 +61,19 @@ def test_failing_rank_is_reported(tmp_path):
     assert launcher.launch(2, [str(script), str(tmp_path), "1"], env=env, timeout=120) == 3
 
 
-def test_bench_refuses_world_mismatch(tmp_path):
-    """Under an external launcher, --gpus must equal WORLD_SIZE (the line's
-    n_gpus is the ranks that ran)."""
+@pytest.mark.gpu
+def test_bench_reports_world_mismatch(built):
+    """Under an external launcher WORLD_SIZE decides the world: a differing
+    --gpus is reported on stderr, the run goes on with the ranks the launcher
+    started and the line's n_gpus is that number (300 nodes x 400 pods, one
+    rank launched with torchrun's variables, --gpus 2)."""
     import subprocess
-    env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode != 0
-    assert "--gpus 2 but the launcher started 1 rank" in r.stderr
+    env = launcher.rank_env({k: v for k, v in os.environ.items() if k not in launcher.LAUNCH_VARS},
+                            0, 1, launcher.free_port())
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+                        "--nodes", "300", "--pods", "400"], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--gpus 2 but the launcher started 1 rank(s); using 1" in r.stderr
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["n_gpus"] == 1 and d["config"]["parallelism"] == "replicas1"
+    assert d["config"]["pods_scheduled_per_step"] == 400 and d["value"] > 0
