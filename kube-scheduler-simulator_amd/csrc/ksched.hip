@@ -946,7 +946,7 @@ int run_spec_persistent(ksg_ctx* ctx, const BatchArgs& b0, int32_t first, int32_
         hi = std::max<int64_t>(hi, (int64_t)q.blob + q.blob_len);
       }
       bytes = 4 * ((cm_words + (size_t)nb * (sizeof(ksg_pod) / 4) + (size_t)(hi - lo) + 3) & ~(size_t)3) +
-              (size_t)kSvSlots * kSvRow * 8 + (size_t)kSvSlots * 64 * 4 + (size_t)64 * (nb + prev_nb) * 4;
+              (size_t)kSvSlots * kSvRow * 8 + (size_t)kSvSlots * 64 * 4 + (size_t)64 * ((nb + prev_nb) | 1) * 4;
       if (bytes <= kSpecLds || nb == 1) break;
       nb = std::max(1, nb / 2);
     }
@@ -1181,7 +1181,7 @@ int run_pipe(ksg_ctx* ctx, int32_t first, int32_t count, int32_t* d_pl, ksg_resu
       }
       if (specw)   // row versions + T as node indices ([pod][nb + carried])
         bytes = 4 * ((cm_words + (size_t)nb * (sizeof(ksg_pod) / 4) + (size_t)(hi - lo) + 3) & ~(size_t)3) +
-                (size_t)kSvSlots * kSvRow * 8 + (size_t)kSvSlots * 64 * 4 + (size_t)64 * (nb + prev_nb) * 4;
+                (size_t)kSvSlots * kSvRow * 8 + (size_t)kSvSlots * 64 * 4 + (size_t)64 * ((nb + prev_nb) | 1) * 4;
       else
         bytes = 4 * ((cm_words + (size_t)nb * (sizeof(ksg_pod) / 4) + (size_t)(hi - lo) + 3) & ~(size_t)3) +
                 (size_t)sblock * slot_bytes;

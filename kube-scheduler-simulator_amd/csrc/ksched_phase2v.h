@@ -32,9 +32,11 @@
 //      pod k* whose decision differs from the speculated one (or that needs the
 //      renormalisation rescan) ends the round: pods before it are committed,
 //      k*'s exact decision is applied (a new version of an existing slot, or a
-//      new slot, evaluated as the next round's first item), the speculated
-//      slots after it are dropped, and the next round speculates from k* + 1
-//      with the pointers restored from k*'s snapshot.
+//      new slot, evaluated as the next round's first item), and the next round
+//      speculates from the first later pod the rollback affects (one that
+//      stepped over k*'s released node, or that holds k*'s new node): the
+//      pods before it keep their decisions, and a pod that takes the same node
+//      again keeps its evaluated column (pod k owns slot nc0 + k throughout).
 //
 // Every decision equals the sequential one: a pod's decision is committed only
 // after verification against the state every earlier committed decision left,
@@ -90,7 +92,8 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
   __shared__ uint8_t s_dptr[64];          // pod's T pointer when it was decided
   __shared__ uint32_t s_owner[kSvOwner];  // lowest lane holding a node (hashed), 0xffffffff = none
   __shared__ SvItem s_item[64 + 1];       // a round's special items: carried slots / the correction
-  __shared__ int32_t s_ctl[8];            // round: start, nv_c, ns_c, n_special; progress; next item
+  __shared__ int32_t s_evnode[64];        // node whose column stands in pod's own slot (-1: none)
+  __shared__ int32_t s_ctl[8];            // round: start, resume pod, first macro-step, n_special; progress; next item
   __shared__ P1Stats s_p1[64];
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -99,7 +102,8 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
   const int nb = a.nb;
   const int cm_words = (((N + 31) / 32) + 3) & ~3;
   constexpr int POD_WORDS = sizeof(ksg_pod) / 4;
-  const int KT = nb + a.k_extra;   // T stride in LDS (entries): K = min(j + 1 + k_extra, nfeas)
+  const int KN = nb + a.k_extra;   // T entries staged per pod: K = min(j + 1 + k_extra, nfeas)
+  const int KT = KN | 1;           // T stride in LDS (entries), odd: the lanes' reads at one pointer fall in different banks
   uint32_t* s_cmask = reinterpret_cast<uint32_t*>(s_dyn);
   ksg_pod* s_pods = reinterpret_cast<ksg_pod*>(s_dyn + cm_words);
   int32_t* s_prog = s_dyn + cm_words + nb * POD_WORDS;
@@ -162,7 +166,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
   {   // T as node indices, [pod][KT]: two keys per 16-byte load, every load issued
       // before the first store; entries past a pod's K are never read (every
       // reader bounds its pointer by K), so they are converted unchecked
-    const int KP = (KT + 1) >> 1;   // key pairs per row
+    const int KP = (KN + 1) >> 1;   // key pairs per row
     constexpr int TI = (64 * kSvSlots / 2 + BLOCK - 1) / BLOCK;
     ulonglong2 kp[TI];
 #pragma unroll
@@ -178,7 +182,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
       const int x = tid + it * BLOCK, q = x / KP, i = 2 * (x - q * KP);
       if (x < nb * KP) {
         s_top[q * KT + i] = key_node(kp[it].x);
-        if (i + 1 < KT) s_top[q * KT + i + 1] = key_node(kp[it].y);
+        if (i + 1 < KN) s_top[q * KT + i + 1] = key_node(kp[it].y);
       }
     }
   }
@@ -192,6 +196,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
   const int nc0 = a.carry ? *a.carry_n : 0;
   if (tid < 64) {
     const int d = a.carry && tid < nc0 ? a.carry[tid] : 0;
+    s_evnode[tid] = -1;
     if (tid < nc0) {
       s_clist[tid] = d;
       s_lastv[tid] = tid;
@@ -232,8 +237,8 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
   }
   if (tid == 0) {
     s_ctl[0] = 0;     // start
-    s_ctl[1] = nc0;   // committed versions
-    s_ctl[2] = nc0;   // committed slots
+    s_ctl[1] = 0;     // the pod the speculation resumes at
+    s_ctl[2] = 0;     // its first macro-step
     s_ctl[3] = nc0;   // special items of round 1: the carried slots
     s_ctl[4] = 0;     // progress: speculation steps published
     s_ctl[6] = 0;     // next verification item to take
@@ -319,6 +324,9 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
     const int32_t stat = p.st + hp.wt * nt + hp.wa * na;
     int32_t fb = 0;
     const bool live = tc_eval<MW>(cm, hp, row, fb) && p1f;
+#ifdef KSG_STAMPS
+    if (lane == 0 && a.stamps) atomicAdd(&a.stamps[10], 1ull);   // row versions evaluated
+#endif
     if (lane > it.t) s_col[it.slot * 64 + lane] = sv_word(stat + fb, live, p1f, ft, fa);
     else if (it.src < 0) s_col[it.slot * 64 + lane] = 0u;
   };
@@ -332,7 +340,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
     cnode = ptr < K ? s_top[lane * KT + ptr] : -1;
     nnode = ptr + 1 < K ? s_top[lane * KT + ptr + 1] : -1;
   }
-  int start = 0, nv_c = nc0, ns_c = nc0, nspecial = nc0;
+  int start = 0, rs = 0, mi0 = 0, nspecial = nc0;
   int guard = 0;
   KSG_STAMP(0);
   while (start < nb && guard++ <= nb) {
@@ -354,9 +362,13 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
       // their candidates at once, exactly as the one-pod steps would (none of
       // them conflicts with an earlier one); then the later pods whose
       // candidate was taken step on.  Pointer snapshots per macro-step; a
-      // rollback restores the one of k*'s macro-step and re-validates.
-      int mi = 0;
-      for (int cur = start; cur < nb; mi++) {
+      // rollback restores the one of the resume pod's macro-step and
+      // re-validates.  The round resumes at pod `rs` (C below): the pods in
+      // [start, rs) keep their decisions and are already published, and the
+      // macro-steps are numbered from mi0 so that the kept pods' snapshots
+      // survive (C keeps mi0 + (nb - rs) <= 64: a macro-step decides >= 1 pod).
+      int mi = mi0;
+      for (int cur = rs; cur < nb; mi++) {
         s_snap[mi * 64 + lane] = (uint8_t)ptr;
         const bool act = lane >= cur && lane < nb && cnode >= 0;
         const int hsh = cnode & (kSvOwner - 1);
@@ -401,7 +413,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
       // ---- V: verify behind the speculation (waves 1.., and wave 0 once S is done) ------
       // items are taken in order from an LDS counter (load balance across the
       // waves); items [0, nspecial): s_item (carried slots / the correction); then
-      // pod k = start + (i - nspecial) once the speculation published it (a
+      // pod k = rs + (i - nspecial) once the speculation published it (a
       // hole, node -1, when the pod took no node).  take(): 1 taken, 0 not
       // published yet (only when !wait), -1 past the end.
       auto take = [&](int i, bool wait, SvItem& it) -> int {
@@ -410,7 +422,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
           it = s_item[i];
           return 1;
         }
-        const int k = start + (i - nspecial);
+        const int k = rs + (i - nspecial);   // (the kept pods [start, rs): every entry below still stands)
         if (k >= nb) return -1;
         // (bounded: every step is published, the bound only keeps a fault from hanging the launch)
         for (unsigned spins = 0;
@@ -420,10 +432,16 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
           __builtin_amdgcn_s_sleep(1);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        const int sl = ns_c + (k - start), v = nv_c + (k - start);
+        const int sl = nc0 + k, v = nc0 + k;   // pod k's own slot and version, the same in every round
         const int pk = s_dptr[k];
         const int d = pk < s_u[k].K ? s_top[k * KT + pk] : -1;   // pod k's speculated node
+        // The node's column already stands in the slot (an earlier round took
+        // the same node): the version is the node's global row + pod k's
+        // deltas and its words depend on (d, k, lane) only, so the row, the
+        // column and every list entry below are still right: nothing to do.
+        if (d >= 0 && s_evnode[k] == d) return 1;
         if (lane == 0) {
+          s_evnode[k] = d;   // (every taken item is finished before the round's barrier)
           s_dec[k] = d;
           s_clist[sl] = d;
           s_lastv[sl] = v;
@@ -468,7 +486,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
     KSG_STAMP(3);
     // ---- A: aggregate every slot present at each pod's turn (wave w: slots w, w + NW, ...)
     {
-      const int ns = ns_c + (nb - start);
+      const int ns = nc0 + nb;   // (slots past the pods' own are never written: pod k's is nc0 + k)
       const bool mine = lane >= start && lane < nb;
       uint32_t dc = 0;   // this wave's slots, in registers; one LDS atomic per pod at the end
       uint64_t bk = 0;
@@ -517,11 +535,11 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
       }
       // the speculated slots of pods k* .. nb - 1 are dropped
       if (mine && lane >= ks && spec >= 0) atomicAnd(&s_cmask[spec >> 5], ~(1u << (spec & 31)));
-      nv_c += ks - start;
-      ns_c += ks - start;
       nspecial = 0;
+      int q1 = nb, m0 = 0;
       if (ks < nb) {
         const int k = ks;
+        const int ns_c = nc0 + k;   // the committed slots: the carried ones and the own slots of the pods before k
         const TcU uk = s_u[k];
         const bool renorm_k = __builtin_amdgcn_readlane((int)renorm, k) != 0;
         int nfeas_k = __builtin_amdgcn_readlane(nfeas, k);
@@ -590,8 +608,12 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
             const uint64_t mk = __ballot(b + lane < ns_c && s_clist[b + lane] == selected);
             if (mk) idx = b + __builtin_ctzll(mk);
           }
+        if (lane == 0) {   // pod k's own slot: a hole unless the correction takes a new node
+          s_clist[ns_c] = -1;
+          s_evnode[k] = -1;
+        }
         if (selected >= 0) {   // the corrected version: the next round's first item
-          const int s = idx >= 0 ? idx : ns_c, v = nv_c;
+          const int s = idx >= 0 ? idx : ns_c, v = ns_c;
           if (lane == 0) {
             s_item[0] = SvItem{selected, s, v, idx >= 0 ? s_lastv[idx] : -1, k};
             if (idx < 0) {
@@ -602,8 +624,6 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
             s_vt[v] = k;
           }
           nspecial = 1;
-          nv_c += 1;
-          if (idx < 0) ns_c += 1;
         }
         if (lane == 0) {
           s_dec[k] = selected;
@@ -615,15 +635,59 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
           res.score_skip = sc ? uk.skip_sc : uk.skip;
           s_res[k] = res;
         }
-        // the next round's speculation: pointers as they were before pod k's step
-        if (lane > k && lane < nb) {
-          ptr = s_snap[s_mstep[k] * 64 + lane];   // at the start of k's macro-step
+        // The rollback changes the taken set in two ways only: pod k's
+        // speculated node Y is released, and its exact node X is taken (when X
+        // is not a committed slot already).  A later pod q decides as before
+        // unless Y stands in T_q before its decided pointer (it would take Y
+        // now) or its own node is X; by induction every pod before the first
+        // affected one, q1, keeps its decision, pointer, macro-step, bitmap bit
+        // and slot, and the next round speculates from q1.
+        const int Y = __builtin_amdgcn_readlane(spec, k);
+        const bool later = lane > k && lane < nb;
+        // Y's place in T_q before the decided pointer (T_q's nodes are distinct).
+        // Y was free when the snapshot of k's macro-step was taken (k held it as
+        // its candidate) and every entry before a snapshot pointer was held
+        // then, so the scan starts there: the few entries stepped over since.
+        int posY = -1;
+        if (later && Y >= 0 && Y != selected) {
+          const int dp = min((int)s_dptr[lane], kSvSlots);
+#pragma unroll 4
+          for (int i = s_snap[s_mstep[k] * 64 + lane]; i < dp; i++) posY = s_top[lane * KT + i] == Y ? i : posY;
+        }
+        const uint64_t am = __ballot(later && (posY >= 0 || (selected >= 0 && idx < 0 && spec == selected)));
+        q1 = am ? __builtin_ctzll(am) : nb;
+        int row = s_mstep[q1 < nb ? q1 : k];   // the snapshot the pods from q1 on restart from
+        m0 = row + 1;                          // (the kept pods' snapshots, rows <= row, must survive)
+        const bool full = q1 < nb && m0 + (nb - q1) > 64;
+        if (full) {   // the snapshot rows would run out: today's full restart, nothing kept
+          q1 = k + 1;
+          m0 = 0;
+          row = s_mstep[k];
+        }
+#ifdef KSG_STAMPS
+        if (tid == 0) st_acc[11] += q1 - (k + 1);   // pods kept across the rollback
+#endif
+        // (every bit from k on was cleared above, before the rescan read the bitmap)
+        if (lane > k && lane < q1 && spec >= 0) atomicOr(&s_cmask[spec >> 5], 1u << (spec & 31));
+        if (lane >= q1 && lane < nb) {
+          // A snapshot pointer is a lower bound: every entry before it is held
+          // by a pod before the snapshot's first one.  The only such holder a
+          // rollback releases is pod k (Y), so a pointer past Y goes back to Y,
+          // in this row and in the rows of the kept pods (a later rollback
+          // among them restarts this lane from one of those).
+          ptr = s_snap[row * 64 + lane];
+          if (posY >= 0) {
+            ptr = min(ptr, posY);
+            if (!full)
+              for (int m = s_mstep[k]; m <= row && m < 64; m++)
+                if (s_snap[m * 64 + lane] > posY) s_snap[m * 64 + lane] = (uint8_t)posY;
+          }
           cnode = ptr < u.K ? s_top[lane * KT + ptr] : -1;
           nnode = ptr + 1 < u.K ? s_top[lane * KT + ptr + 1] : -1;
-          // re-validate: nodes the committed pods of that macro-step took, and a
-          // new node taken by pod k (the rescan's choice), are stepped over
+          // re-validate: nodes the kept and committed pods took since, and a
+          // new node taken by pod k, are stepped over (at most K <= kSvSlots entries)
           bool conflict = cnode >= 0 && sv_changed(s_cmask, cnode);
-          while (conflict) {
+          for (int g = 0; conflict && g < kSvSlots; g++) {
             ptr++;
             cnode = nnode;
             nnode = ptr + 1 < u.K ? s_top[lane * KT + ptr + 1] : -1;
@@ -633,10 +697,10 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
       }
       if (lane == 0) {
         s_ctl[0] = ks < nb ? ks + 1 : nb;
-        s_ctl[1] = nv_c;
-        s_ctl[2] = ns_c;
+        s_ctl[1] = q1;
+        s_ctl[2] = m0;
         s_ctl[3] = nspecial;
-        s_ctl[4] = 0;
+        s_ctl[4] = ks < nb ? q1 - (ks + 1) : 0;   // the kept pods are published at once
         s_ctl[6] = 0;
       }
     }
@@ -644,8 +708,8 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
     __syncthreads();
     KSG_STAMP(6);
     start = s_ctl[0];
-    nv_c = s_ctl[1];
-    ns_c = s_ctl[2];
+    rs = s_ctl[1];
+    mi0 = s_ctl[2];
     nspecial = s_ctl[3];
   }
   if (tid == 0 && start < nb) {   // cannot happen: each round commits >= 1 pod
@@ -664,6 +728,7 @@ __device__ __forceinline__ void spec_walk_batch(const BatchArgs& a) {
     }
   }
   __syncthreads();
+  const int ns_c = nc0 + nb;   // every slot: the carried ones and each pod's own
   for (int x = tid; x < ns_c * SW; x += BLOCK) {
     const int s = x / SW, w = x - s * SW, node = s_clist[s];
     if (node < 0) continue;
